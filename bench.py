@@ -7,6 +7,12 @@ across the N ranks: "scaling" is strong. Random-init Qwen2.5-0.5B weights, synth
 
   python bench.py [--gpus N] [--steps K] [--warmup W]          (N>1 under torch.distributed.run)
 
+A plain run sets up, runs W warmup steps, times K steps and prints one JSON line from what those steps
+recorded; no further run follows them. ``--dump-outputs DIR`` also writes what the last timed step computed
+(``dump_outputs`` below) so that two builds can be compared output for output; the prompts, the initial weights, the sampling and the rewards are all
+seeded, so the inputs of a run depend on its arguments alone. ``--full`` adds the side figures that take runs of
+their own after the timed steps: ``roofline_k1`` / ``roofline_k1_two_pass`` and ``cpu_baseline`` (null otherwise).
+
 Besides the step rate the JSON line carries
   roofline     : the dominant eagerly launched hand-written kernel (--roofline-kernel; default drl_gemm, the
                  stream-K ping-pong GEMM that runs every projection of the full-sequence passes — forward,
@@ -17,7 +23,7 @@ Besides the step rate the JSON line carries
                  duration, against its bound's peak (2.5 PFLOP/s dense bf16 MFMA or 8 TB/s HBM);
                  traffic = HBM bytes per launch from the committed rocprofv3 PMC pass
                  (profiles/pmc_<kernel>.json, FETCH_SIZE doubled per the gfx950 correction + WRITE_SIZE) or null;
-  cpu_baseline : rank 0 at N=1 only — oracle/cpu_baseline.py (the same step restated in eager torch fp32
+  cpu_baseline : --full, rank 0 at N=1 only — oracle/cpu_baseline.py (the same step restated in eager torch fp32
                  on the host cores) on a bounded sample, scaled to PPO steps/s.
 """
 
@@ -202,6 +208,59 @@ def cpu_baseline(cfg):
     return out
 
 
+DUMP_LIMIT_BYTES = 64 << 20  # --dump-outputs: everything written, in total
+DUMP_SAMPLE = 1 << 20  # elements kept of an output larger than its share (fixed, seeded positions)
+DUMP_SEED = 0xD0755
+# metrics that restate wall time (stage timings, throughputs, MFU): what the step measured, not what it computed
+_TIMED_METRICS = ("timing_s/", "timing_per_token_ms/", "perf/")
+
+
+def dump_outputs(dirname, trainer, metrics):
+    """--dump-outputs: what the last timed ``trainer.step`` handed back, as ``<name>.npy`` (float32 / float64).
+
+    ``metric.<key>``  every scalar of the step's metrics dict that is computed, not timed (one float64 each; ``/``
+                      in a key becomes ``.``);
+    ``batch.<key>``   every tensor of the step's batch (``trainer.last_batch``: token ids, masks, old / ref
+                      log-probs, rewards, advantages, returns), float32 (integer ids and masks are exact in it
+                      below 2^24);
+    ``actor.master``  the actor's fp32 master weights after the step's updates.
+    An array larger than its share of the 64 MB limit is written as a sample at DUMP_SAMPLE positions drawn once
+    from DUMP_SEED, the same for every run of the same shapes."""
+    import numpy as np
+    import torch
+
+    os.makedirs(dirname, exist_ok=True)
+    arrays = {}
+    for k in sorted(metrics):
+        v = metrics[k]
+        if k.startswith(_TIMED_METRICS) or isinstance(v, (str, bytes)):
+            continue
+        a = np.asarray(v.detach().cpu().numpy() if isinstance(v, torch.Tensor) else v)
+        if a.dtype.kind in "fiub":
+            arrays["metric." + k.replace("/", ".")] = a.astype(np.float64)
+    batch = getattr(trainer, "last_batch", None)
+    tensors = {}
+    if batch is not None and batch.batch is not None:
+        tensors.update({"batch." + k: v for k, v in batch.batch.items()})
+    store = getattr(getattr(getattr(trainer, "actor_rollout_wg", None), "worker", None), "store", None)
+    if getattr(store, "master", None) is not None:
+        tensors["actor.master"] = store.master
+    share = (DUMP_LIMIT_BYTES - sum(a.nbytes for a in arrays.values())) // max(1, len(tensors))
+    for name in sorted(tensors):
+        t = tensors[name].detach().reshape(-1)
+        if t.numel() * 4 > share:
+            g = torch.Generator(device="cpu").manual_seed(DUMP_SEED)
+            n = min(DUMP_SAMPLE, share // 4)
+            idx = torch.randint(0, t.numel(), (n,), generator=g).sort().values
+            t = t[idx.to(t.device)]
+        arrays[name.replace("/", ".")] = t.to(torch.float32).cpu().numpy()
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= DUMP_LIMIT_BYTES, total
+    for name, a in arrays.items():
+        np.save(os.path.join(dirname, name + ".npy"), a)
+    return total
+
+
 def build_config(args):
     from dots.rl_amd.config import apply_overrides, default_config
 
@@ -247,7 +306,13 @@ def main():
     # 0.36 s (profiles/r03_decode_lanes.jsonl, warmup-1 runs)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--tiny", action="store_true", help="2-layer model, small batch (bring-up only)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the side figures that take runs of their own: the K1 "
+                         "rooflines at 2^26 tokens and the CPU baseline (a plain run leaves them null)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the last timed step computed as DIR/<name>.npy (float32 / float64, at most "
+                         "64 MB in all; see dump_outputs)")
     ap.add_argument("--roofline-kernel", default="drl_gemm", choices=sorted(ROOFLINE))
     ap.add_argument("--override", nargs="*", default=[])
     ap.add_argument("--dapo", action="store_true",
@@ -321,6 +386,8 @@ def main():
     gen_tokens = sum(h["perf/total_num_tokens"] for h in hist)  # prompt + response tokens processed
     resp_tokens = sum(h["perf/rollout_tokens_per_sec"] * h["timing_s/gen"] for h in hist)
     gen_time = sum(h["timing_s/gen"] for h in hist)
+    if args.dump_outputs and rank == 0 and hist:
+        dump_outputs(args.dump_outputs, trainer, hist[-1])
     n_launch, t_launch, b_launch = timer.summary()
     # the rate of the kernel's work while any of its launches runs: launches on the side stream (weight gradients)
     # overlap the current stream's, so the mean per-launch interval (mean_launch_us, comparable to rocprof's
@@ -412,11 +479,11 @@ def main():
                        "timed_device_allocs": ms1.get("num_device_alloc", 0) - ms0.get("num_device_alloc", 0),
                        "timed_device_frees": ms1.get("num_device_free", 0) - ms0.get("num_device_free", 0)},
         }
-        if not args.tiny:
+        if args.full and not args.tiny:
             # the actor's form: update_policy hands K1 every micro-batch's sum(response_mask) (one pass over HBM)
             line["roofline_k1"] = k1_roofline("one_pass")
             line["roofline_k1_two_pass"] = k1_roofline("two_pass")
-        if world == 1 and not args.no_cpu_baseline and not args.tiny:
+        if args.full and world == 1 and not args.no_cpu_baseline and not args.tiny:
             line["cpu_baseline"] = cpu_baseline(cfg)
         print(json.dumps(line), flush=True)
     dist.destroy_process_group()

@@ -1,6 +1,8 @@
-"""The verl-side plug point (dots.rl_amd/verl_adapter.py) against the reference's own decorator / worker /
-DataProto code. Skipped where /root/reference is absent (the GPU box); the checks run in
-a child process so the reference's import stubs never enter this session (tests/verl_adapter_check.py)."""
+"""The verl-side plug point (dots.rl_amd/verl_adapter.py) against verl's decorator / worker / DataProto surface
+(VERDICT r01 item 7): the dispatch mode, execute mode and blocking flag of every hot-path method equal what verl's
+own FSDP workers register, and the patched forward keeps verl's signature (both recorded from a verl checkout in
+tests/golden/verl_api.json). The checks run in a child process so the ``verl`` modules they install never enter
+this session (tests/verl_adapter_check.py, which can also run them against a verl checkout itself)."""
 
 import os
 import subprocess
@@ -11,7 +13,6 @@ import pytest
 HERE = os.path.dirname(os.path.abspath(__file__))
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/verl"), reason="needs the reference checkout")
 def test_adapter_matches_reference_dispatch_and_dataproto():
     env = dict(os.environ, PYTHONDONTWRITEBYTECODE="1")
     r = subprocess.run([sys.executable, os.path.join(HERE, "verl_adapter_check.py")], capture_output=True, text=True,

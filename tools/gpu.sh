@@ -6,7 +6,7 @@
 #   tests                       the whole -m gpu suite
 #   tests:<a>,<b>,...           the named pytest targets (files or node ids), -m gpu, verbose
 #   bench[:<steps>[:<warmup>]]  the default bench line (no CPU baseline) + the last step's drl_gemm launch log
-#   benchfull                   the driver's bench command (python bench.py, CPU baseline included)
+#   benchfull                   the bench with its side figures (python bench.py --full: K1 rooflines, CPU baseline)
 #   benchfused                  the bench with model.use_fused_kernels=True
 #   benchenv:<name>:<V=x>,...   the bench (5 steps, 2 warmup) with environment switches -> bench_<name>.json
 #   bench64                     the per-rank workload of N = 8 (64 sequences) ; bench128 / bench256 likewise
@@ -55,7 +55,7 @@ for step in "$@"; do
         || { tail -20 "$OUT/bench.err"; exit 1; }
       cat "$OUT/bench.json" ;;
     benchfull)
-      timeout -k 10 600 python -u bench.py > "$OUT/benchfull.json" 2> "$OUT/benchfull.err" \
+      timeout -k 10 600 python -u bench.py --full > "$OUT/benchfull.json" 2> "$OUT/benchfull.err" \
         || { tail -20 "$OUT/benchfull.err"; exit 1; }
       cat "$OUT/benchfull.json" ;;
     benchfused)  # model.use_fused_kernels=True (A21 forward + the vocabulary-blocked HIP backward)
